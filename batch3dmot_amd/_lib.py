@@ -294,6 +294,14 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def forks_allowed() -> bool:
+    """Whether work may be forked onto a side stream here.  HIP runs the parallel branches of a launched hipGraph on streams
+    of its own, and with fewer than four hardware queues per process (GPU_MAX_HW_QUEUES, default 4) the launch of such a
+    graph segfaults in the runtime (the run dies at 2 and 3).  So inside a stream capture under such a budget
+    every side-stream branch runs on the capturing stream instead: same kernels, same order within each branch."""
+    return not (torch.cuda.is_current_stream_capturing() and int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) < 4)
+
+
 def current_stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 

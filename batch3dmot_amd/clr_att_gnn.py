@@ -147,12 +147,13 @@ class _GNNFunction(torch.autograd.Function):
         dev = pose_feats.device
         N, E = graph.N, graph.E
         nl, nr = int(lidar_nodes.numel()), int(radar_nodes.numel())
+        single = module.single_stream or not _lib.forks_allowed()
         flags = ((B3D_FLAG_TRAINING if training else 0) | (B3D_FLAG_RUN_DEAD_KNN if module.run_dead_knn else 0)
-                 | (B3D_FLAG_SINGLE_STREAM if module.single_stream else 0)
+                 | (B3D_FLAG_SINGLE_STREAM if single else 0)
                  | (0 if getattr(module, "run_dead_last_messages", True) else B3D_FLAG_SKIP_DEAD_LAST_MESSAGES))
         # optional: let the discarded k-NN block run on under the loss and the backward sweep (measured on
         # MI355X: 4 % slower than joining at the end of forward -- it delays the start of every backward kernel)
-        defer = bool(training and module.run_dead_knn and not module.single_stream and module.defer_knn_join)
+        defer = bool(training and module.run_dead_knn and not single and module.defer_knn_join)
         if defer:
             flags |= B3D_FLAG_DEFER_SIDE_JOIN
         nbytes = lib.b3d_clr_workspace_bytes(N, E, nl, nr, module.depth, flags)
@@ -614,7 +615,7 @@ class GNN(nn.Module):
         # never reused while an earlier consumer reads it.
         dev = img_feats.device
         side = pn = None
-        if self.encoder_streams and img_feats.is_cuda:
+        if self.encoder_streams and img_feats.is_cuda and _lib.forks_allowed():
             streams = _ENC_STREAMS.get(dev)          # per device, shared by all models of the process (a module attribute would
             if streams is None:                      # make the module impossible to deepcopy / pickle once it has run)
                 streams = _ENC_STREAMS[dev] = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))

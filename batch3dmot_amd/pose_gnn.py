@@ -108,11 +108,12 @@ class _PoseGNNFunction(torch.autograd.Function):
         lib = _lib.load()
         dev = pose_feats.device
         N, E = graph.N, graph.E
+        single = module.single_stream or not _lib.forks_allowed()
         flags = ((B3D_FLAG_TRAINING if training else 0) | (B3D_FLAG_RUN_DEAD_KNN if module.run_dead_knn else 0)
-                 | (B3D_FLAG_SINGLE_STREAM if module.single_stream else 0))
+                 | (B3D_FLAG_SINGLE_STREAM if single else 0))
         # optional: let the discarded k-NN block run on under the loss and the backward sweep (measured on
         # MI355X: 4 % slower than joining at the end of forward -- it delays the start of every backward kernel)
-        defer = bool(training and module.run_dead_knn and not module.single_stream and module.defer_knn_join)
+        defer = bool(training and module.run_dead_knn and not single and module.defer_knn_join)
         if defer:
             flags |= B3D_FLAG_DEFER_SIDE_JOIN
         nbytes = lib.b3d_pose_workspace_bytes(N, E, module.depth, flags)

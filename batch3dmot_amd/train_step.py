@@ -154,6 +154,19 @@ class EncodeAhead:
         self.stream = None
         self.pending = None
 
+    def _fork(self, dev):
+        """The stream this object's work goes to, ordered behind the current stream: its side stream, or -- inside a capture
+        without room for parallel graph branches (``_lib.forks_allowed``) -- the current stream itself."""
+        from . import _lib
+        cur = torch.cuda.current_stream(dev)
+        if not _lib.forks_allowed():
+            self.stream = cur
+            return cur
+        if self.stream is None or self.stream.device != dev or self.stream == cur:
+            self.stream = torch.cuda.Stream(dev)
+        self.stream.wait_stream(cur)
+        return self.stream
+
     _SLOTS = {"img": (0,), "lidar": (1, 2), "radar": (3, 4), "points": (1, 2, 3, 4), "all": (0, 1, 2, 3, 4)}
 
     def launch(self, data, rows=None, static=None, parts: str = "all"):
@@ -166,16 +179,13 @@ class EncodeAhead:
         if self.pending is not None and (self.pending[0] is not data or parts == "all" or any(k in self.pending[1] for k in self._SLOTS[parts])):
             raise RuntimeError("EncodeAhead.launch: the previous batch was never taken (or this part of the batch was launched already)")
         dev = data.pose_feats.device
-        if self.stream is None or self.stream.device != dev:
-            self.stream = torch.cuda.Stream(dev)
-        cur = torch.cuda.current_stream(dev)
-        self.stream.wait_stream(cur)
+        side = self._fork(dev)
         if rows is None and parts != "img":
             rows = self.gnn.modality_rows(data)              # (on the caller's side: the counts are shapes)
         keep = self.gnn.encoder_streams
         self.gnn.encoder_streams = False                     # one branch: no forks inside the side stream
         try:
-            with torch.cuda.stream(self.stream):
+            with torch.cuda.stream(side):
                 st = static if static is not None else (None,) * 5       # the big outputs go straight into their static buffers
                 if parts == "all":
                     out = [self.gnn._encode_img(data, out=st[0])] + list(self.gnn._encode_lidar(data, rows[0], out=st[1])) \
@@ -203,7 +213,7 @@ class EncodeAhead:
                     out = [static[k] for k in slots]
                 if rows is not None and not torch.cuda.is_current_stream_capturing():
                     for t in rows:
-                        t.record_stream(self.stream)          # produced elsewhere, read by this stream's gathers
+                        t.record_stream(side)                 # produced elsewhere, read by this stream's gathers
         finally:
             self.gnn.encoder_streams = keep
         have = dict(self.pending[1]) if self.pending is not None else {}
@@ -217,16 +227,13 @@ class EncodeAhead:
         only.  Left in ``data._b3d_graph``, where ``GNN.forward`` looks for it; ``take`` joins the side stream.  ``ws``: a caller-owned
         ``uint8`` buffer of ``_lib.Graph.workspace_bytes(N, E)`` bytes (fixed addresses, for hipGraph-captured steps)."""
         from . import _lib
-        dev = data.pose_feats.device
-        if self.stream is None or self.stream.device != dev:
-            self.stream = torch.cuda.Stream(dev)
-        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        side = self._fork(data.pose_feats.device)
         ei = data.edge_index
-        with torch.cuda.stream(self.stream):
+        with torch.cuda.stream(side):
             g = _lib.Graph(ei if ei.is_contiguous() else ei.contiguous(), data.pose_feats.size(0),
                            validated=getattr(data, "_b3d_valid_edge_index", None) is ei, ws=ws)
             if not torch.cuda.is_current_stream_capturing():
-                ei.record_stream(self.stream)
+                ei.record_stream(side)
         data._b3d_graph = g
         self._graph_for = data
         return g
@@ -235,11 +242,7 @@ class EncodeAhead:
         """The NEXT batch's modality row ids on the side stream, written into ``static_rows`` with the counts checked on the device
         (``GNN.modality_rows_into``): the prologue of a hipGraph-captured step without a host read-back.  Call before the
         ``launch(..., rows=static_rows)`` calls that consume them (same stream: ordered)."""
-        dev = data.pose_feats.device
-        if self.stream is None or self.stream.device != dev:
-            self.stream = torch.cuda.Stream(dev)
-        self.stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(self.stream):
+        with torch.cuda.stream(self._fork(data.pose_feats.device)):
             self.gnn.modality_rows_into(data, static_rows, mismatch)
 
     def take(self, data):
@@ -251,7 +254,8 @@ class EncodeAhead:
         out = tuple(have[k] for k in range(5))
         self.pending = None
         cur = torch.cuda.current_stream(data.pose_feats.device)
-        cur.wait_stream(self.stream)
+        if self.stream is not None and self.stream != cur:
+            cur.wait_stream(self.stream)
         if not is_static and not torch.cuda.is_current_stream_capturing():
             for t in out:
                 t.record_stream(cur)

@@ -481,7 +481,7 @@ _SKIP_PRE = os.environ.get("B3D_SKIP_PRE", "0") == "1"      # diagnostic only: t
 
 def run_step(wl, graphs, opt_graph, split, i, stamps=None):
     """Step i of the timed region: the eager part in front of the replay (`pre`), the replay(s), and at N > 1 the eager
-    flat all-reduce between them; or the eager step when nothing was captured."""
+    flat all-reduce between them; or the eager step when nothing was captured.  Returns the step's (loss, scores, aux)."""
     if graphs is not None:
         t0 = time.perf_counter()
         if not _SKIP_PRE:
@@ -494,8 +494,8 @@ def run_step(wl, graphs, opt_graph, split, i, stamps=None):
             # the flat gradient buffer was written by the replay
             wl.sync.sync(force=True, force_collective=getattr(wl, "force_collective", False))
             opt_graph.replay()
-    else:
-        wl.step(i)
+        return wl.cap_ret[i % len(wl.pool)]
+    return wl.step(i)
 
 
 def snapshot(wl):
@@ -540,6 +540,30 @@ def state_digest(wl):
             **({"adam.step": wl.opt.step_dev.clone()} if getattr(wl.opt, "step_dev", None) is not None else {})}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(wl, ret):
+    """Host float32 copies of what a caller of the step receives: the loss, the edge scores and the node tensor the model
+    returns beside them (train_step's (loss, out, aux)), and the model state the step leaves (parameters after Adam,
+    BatchNorm statistics), flattened in state_dict order."""
+    torch.cuda.synchronize()
+    loss, scores, aux = ret
+    out = {"loss": loss, "scores": scores, "aux": aux,
+           "model_state": torch.cat([v.detach().reshape(-1).float() for v in wl.model.state_dict().values() if v.is_floating_point()])}
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(outputs, path):
+    import numpy as np
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def loss_check(wl, graphs, i):
     """What the timed region computes, checked against the eager step: from the same state, replay step i (with its eager
     prologue) and read the loss out of the graph's static tensor; restore; run the eager step on the same batch.  The two
@@ -573,9 +597,10 @@ def collective_check(wl, graphs, opt_graph, i):
     return {"tensors": len(a), "equal": not bad, "differing": bad[:5]}
 
 
-def measure(wl: Workload, args, world, dist, steps, warmup, ramp_ms, use_graph):
+def measure(wl: Workload, args, world, dist, steps, warmup, ramp_ms, use_graph, keep_outputs=False):
     """W instrumented warm-up steps, optional hipGraph capture, untimed clock ramp, K timed steps (barrier +
-    synchronize on both sides), eager instrumented pass.  Returns a dict of raw measurements."""
+    synchronize on both sides), eager instrumented pass.  Returns a dict of raw measurements; with keep_outputs also
+    "outputs", host copies of what the last timed step computed (step_outputs)."""
     dev = wl.dev
     pool_n = len(wl.pool)
     stub = wl.kind == "stub"
@@ -636,10 +661,13 @@ def measure(wl: Workload, args, world, dist, steps, warmup, ramp_ms, use_graph):
     stamps = []
 
     def timed_step(i):
-        run_step(wl, graphs, opt_graph, split, i, stamps)
+        return run_step(wl, graphs, opt_graph, split, i, stamps)
 
     # Clock ramp (untimed): a fresh box idles at ~550 MHz; keep the GPU busy until ramp_ms have passed, the same
-    # number of steps on every rank (each holds a collective).
+    # number of steps on every rank (each holds a collective).  The ramp's step count depends on the clock, so when the
+    # outputs are kept the state in front of it is restored after it: the timed steps then start from the same state
+    # in every run with the same arguments.
+    pinned = snapshot(wl) if keep_outputs else None
     ramp_steps = 0
     if ramp_ms > 0 and world > 1:
         ramp_steps = max(8, int(ramp_ms / 10.0) // 8 * 8)
@@ -653,6 +681,9 @@ def measure(wl: Workload, args, world, dist, steps, warmup, ramp_ms, use_graph):
                 timed_step(i)
             torch.cuda.synchronize()
             ramp_steps += 4
+    if pinned is not None:
+        restore(wl, pinned)
+        del pinned
     trace(f"ramp done ({ramp_steps} steps)")
     # one event per step boundary (K + 1 records on the launch stream, no synchronisation): per-step durations for the
     # median beside the contract's mean
@@ -664,7 +695,7 @@ def measure(wl: Workload, args, world, dist, steps, warmup, ramp_ms, use_graph):
     marks[0].record()
     del stamps[:]
     for i in range(steps):
-        timed_step(warmup + i)
+        last = timed_step(warmup + i)
         marks[i + 1].record()
     # Host time to enqueue the K steps (diagnostic): the GPU's rate, not the host's cost -- the eager prologue reads the modality
     # counts back (`.item()`: it returns when the mask kernels have run, and those queue behind the previous replay), and a bare
@@ -683,6 +714,8 @@ def measure(wl: Workload, args, world, dist, steps, warmup, ramp_ms, use_graph):
                            "GNN.modality_rows_into): the timed region is invalid")
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
     trace(f"timed region done: {1e3 * dt / steps:.3f} ms/step")
+    # copied before the checks below, which restore and re-step the state
+    outputs = step_outputs(wl, last) if keep_outputs else None
     # the replayed step against the eager step, from the same state (N = 1: at N > 1 a step holds a collective)
     lc = None
     if graphs is not None and not split:
@@ -719,7 +752,7 @@ def measure(wl: Workload, args, world, dist, steps, warmup, ramp_ms, use_graph):
     my_edges = sum(wl.edges[(warmup + i) % pool_n] for i in range(steps))
     return {"dt": dt, "edges": my_edges, "t_enqueue": t_enqueue, "t_first": t_first, "t_pre": t_pre, "fam_all": fam_all, "fam": fam, "dom": dom,
             "graphs": graphs is not None, "graph_note": graph_note, "ramp_steps": ramp_steps, "pair_us": pair_us,
-            "step_ms": step_ms, "loss_check": lc}
+            "step_ms": step_ms, "loss_check": lc, "outputs": outputs}
 
 
 def mfma_peak(bf_frac):
@@ -904,7 +937,13 @@ def main():
                     help="N = 1 only: initialise the process group with ONE rank and run the N > 1 timed region (forward + backward "
                          "graph | flat all-reduce on the launch stream | optimizer graph) -- executes RCCL next to the captured graphs "
                          "on a 1-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="training: write what the last timed step computed (loss, scores, aux, model state) as DIR/<name>.npy "
+                         "(float32; rank 0).  The timed steps then start from the state the warm-up left, whatever the clock ramp "
+                         "ran, so runs with the same arguments get the same inputs")
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode != "train" or args.stub_cpu):
+        raise SystemExit("--dump-outputs: training runs on the GPU only")
     # training: encode-ahead unless --serial-encoders; inference: only on request
     args.encode_ahead = args.encode_ahead_flag if args.mode == "infer" else not args.serial_encoders
 
@@ -946,7 +985,10 @@ def main():
             raise SystemExit("--scaling strong: the global batch of 16 graphs must divide over the ranks")
         graphs_per_gpu = 16 // world
     wl = Workload(args.model, dev, rank, world, args, encoders=args.encoders, graphs=graphs_per_gpu, modalities=args.modalities)
-    m = measure(wl, args, world, dist, args.steps, args.warmup, args.ramp_ms, use_graph=not args.no_graph)
+    m = measure(wl, args, world, dist, args.steps, args.warmup, args.ramp_ms, use_graph=not args.no_graph,
+                keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(m["outputs"], args.dump_outputs)
 
     dt, total_edges = reduce_over_ranks(m, dev, world, dist)
 
