@@ -32,6 +32,10 @@ constexpr int kTileRows = kWaves * kRowsPerWave;   // 128 rows per workgroup til
 constexpr int kWBufFloats = 13312;        // one weight ring slot: 52 KB
 constexpr int kChunkAlign = 256;          // floats; 1 KB = one wave-wide 16-byte LDS-DMA
 constexpr int kLdsBytes = 2 * kWBufFloats * 4;
+// Edges per aligned block of the camera+LiDAR+radar `past` run sums: the edge kernels add each destination's run inside one
+// such block (b3d_estream.hpp run_sums, static_asserts there) and the graph build lists one tail row per (destination, block)
+// run (b3d_prep.hip graph_past_lists).  Both sides must agree on it.
+constexpr int kPastBlock = 16;
 
 __host__ __device__ constexpr int round_up(int a, int b) { return (a + b - 1) / b * b; }
 __host__ __device__ constexpr int pad16(int a) { return round_up(a, 16); }

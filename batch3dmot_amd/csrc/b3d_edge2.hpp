@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kWaves * 64, kWgPerCu) void edge_fwd_kernel(const E
     unsigned row[kRB], rc[kRB], s[kRB], d[kRB];
 #pragma unroll
     for (int rb = 0; rb < kRB; ++rb) {
-      row[rb] = (unsigned)tile * (unsigned)kTileRows + (ring.wave * kRB + rb) * 16 + (lane & 15);
+      row[rb] = (unsigned)tile * (unsigned)kTileRows + (ring.wave * kRB + rb) * kRowBlock + (lane & (kRowBlock - 1));
       rc[rb] = row[rb] < (unsigned)a.E ? row[rb] : (unsigned)a.E - 1u;         // rows past the end compute on the last edge
       s[rb] = (unsigned)a.src[rc[rb]]; d[rb] = (unsigned)a.dst[rc[rb]];
     }
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(kWaves * 64, kWgPerCu) void edge_bwd_kernel(const E
     unsigned row[kRB], rc[kRB];
 #pragma unroll
     for (int rb = 0; rb < kRB; ++rb) {
-      row[rb] = (unsigned)tile * (unsigned)kTileRows + (ring.wave * kRB + rb) * 16 + (lane & 15);
+      row[rb] = (unsigned)tile * (unsigned)kTileRows + (ring.wave * kRB + rb) * kRowBlock + (lane & (kRowBlock - 1));
       rc[rb] = row[rb] < (unsigned)a.E ? row[rb] : (unsigned)a.E - 1u;
     }
     v4f de[kRB][EB];

@@ -61,7 +61,8 @@ constexpr int kRB = B3D_ES_RB;
 #define B3D_ES_LATE 0
 #endif
 constexpr bool kLate = B3D_ES_LATE != 0;
-constexpr int kWaves = B3D_ES_WAVES, kTileRows = kWaves * 16 * kRB;    // rows per workgroup
+constexpr int kRowBlock = 16;                                          // rows of a row block: lane m of DPP row q holds row m
+constexpr int kWaves = B3D_ES_WAVES, kTileRows = kWaves * kRowBlock * kRB;    // rows per workgroup
 constexpr int kWgPerCu = (kRB == 1 && kWaves == 4) ? 2 : 1;
 constexpr int kChunkSteps = 4, kStepBytes = 6144, kChunkBytes = kChunkSteps * kStepBytes, kSlots = B3D_ES_SLOTS;
 constexpr int kPiecesPerWave = kChunkBytes / 1024 / kWaves;  // 6
@@ -466,6 +467,11 @@ __device__ __forceinline__ bool run_sums(v4f (&v)[NB], int key) {
   run_scan_step<NB, 8>(v, key);
   return __builtin_amdgcn_update_dpp(-1, key, 0x100 + 1, 0xf, 0xf, false) != key;     // row_shl:1: the key of lane m + 1 (-1 behind lane 15)
 }
+// The graph build lists the tail of every (destination, aligned kPastBlock-edge block) run as the row that holds the run's sum
+// (b3d_prep.hip graph_past_lists): its blocks must be exactly the row blocks summed here -- one DPP row, whose four shifts above
+// reach lanes 1 .. 15 back -- and, tiles starting at multiples of kTileRows, no tile may begin inside a block.
+static_assert(kRowBlock == 16 && kPastBlock == kRowBlock, "run_sums sums one 16-lane DPP row: the graph build's kPastBlock must match");
+static_assert(kTileRows % kPastBlock == 0, "a tile must start on a run block boundary");
 
 // the same row table access for every row block of the wavefront
 template <int NB>

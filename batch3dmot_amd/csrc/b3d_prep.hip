@@ -99,8 +99,7 @@ __global__ __launch_bounds__(256) void graph_sort_segments(const int* __restrict
 
 // The rows of `past` the node kernel sums per node (b3d.h: b3d_graph.past_ptr / past_rows): with edges grouped by destination, the
 // last edge of every (destination, aligned 16-edge block) run -- the edge kernel has added the run there --, otherwise every edge of the
-// destination's list.  One workgroup: a scan over the nodes in chunks of 1,024.
-constexpr int kPastBlock = 16;                  // rows of a wavefront of the edge kernels (b3d_estream.hpp)
+// destination's list.  One workgroup: a scan over the nodes in chunks of 1,024.  (kPastBlock: b3d_dev.hpp)
 __global__ __launch_bounds__(1024) void graph_past_lists(const int* __restrict__ dst_ptr, const int* __restrict__ dst_perm, int N,
                                                          const int* __restrict__ unsorted, int* __restrict__ past_ptr,
                                                          int* __restrict__ past_rows) {

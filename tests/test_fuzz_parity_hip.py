@@ -19,3 +19,15 @@ def test_seeded_random_graphs_match_the_oracle():
     assert len(lines) >= 12
     assert bad == 0, "\n".join(lines)
     assert worst_out < 1e-4, (worst_out, lines)
+
+
+@pytest.mark.gpu
+def test_seeded_irregular_graphs_match_the_oracle():
+    """The same sweep on irregular graphs (fuzz_parity.make_irregular): every case adds a hub of in-degree 20 .. 300 (a `past` run over
+    many 16-edge blocks and tiles) and / or a source of out-degree 20 .. 300 to the window, and half of them shuffle the edge order."""
+    import fuzz_parity
+    lines = []
+    bad, worst_out, worst_l2 = fuzz_parity.run_cases(cases=8, seed=23, max_nodes=400, out=lines.append, topology="irregular")
+    assert len(lines) >= 8 and sum("shuffled" in s for s in lines) == 4 and all("hub" in s for s in lines)
+    assert bad == 0, "\n".join(lines)
+    assert worst_out < 1e-4, (worst_out, lines)

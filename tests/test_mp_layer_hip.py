@@ -121,29 +121,50 @@ def test_clr_layer_forward_backward_match_oracle(n, k):
     """clr_att_gnn.py:227-356 as an operator of its own: outputs, the gradients of all five inputs (x, initial_x,
     edge_attr, att_edge_attr) and of the ten Linear layers against the CPU oracle, every entry at 1e-4 on inputs whose
     ReLU pre-activations all stay clear of zero (data-dependent masks, up to the benchmark's 3,000 nodes / ~31,000 edges)."""
+    d = _graph(n, k, 13)
+    _clr_layer_against_oracle(d.pose_feats.size(0), d.edge_index, margin=1e-4 if n < 3000 else 3e-5)
+
+
+@pytest.mark.parametrize("topo", ["t1", "t2", "t3", "t7_t1_shuffled", "t7_t1_reversed", "t7_t2_shuffled", "t7_t2_reversed"])
+def test_clr_layer_irregular_topologies(topo):
+    """The same flow on the hand-made graphs of tests/irregular_graphs.py: T1 (runs that fill a whole 16-edge block or start at
+    many offsets inside one, up to five blocks per run), T2 (a destination with 300 in-edges: 19+ blocks over 5+ tiles), T3 (a
+    source with 250 out-edges, sources with out-degree 1 .. 4) and T7 (T1 and T2 out of destination order).  A wrong per-node sum of
+    the `past` runs or of the three parts of a `future` list shows in x' directly."""
+    import irregular_graphs as ig
+    base = {"t1": ig.block_runs, "t2": ig.long_run, "t3": ig.out_hub}
+    name = topo.split("_")[-2] if topo.startswith("t7") else topo
+    n, ei = base[name]()
+    if topo.endswith("shuffled"):
+        ei = ig.shuffled(ei, 7)
+    elif topo.endswith("reversed"):
+        ei = ig.reversed_order(ei)
+    _clr_layer_against_oracle(n, ei)
+
+
+def _clr_layer_against_oracle(N, edge_index, margin=1e-4):
     from batch3dmot_amd.clr_att_gnn import CausalMessagePassing
     dev = torch.device("cuda:0")
-    d = _graph(n, k, 13)
     ora = ref_torch.CausalMessagePassing("clr")
     seeded_fill_(ora, 8)
     m = CausalMessagePassing()
     m.load_state_dict(ora.state_dict())
     m.to(dev)
     g = torch.Generator().manual_seed(3)
-    N, E = d.pose_feats.size(0), d.edge_index.size(1)
+    E = edge_index.size(1)
     x, x0 = torch.randn(N, 96, generator=g), torch.randn(N, 96, generator=g)
     e, att = torch.randn(E, 64, generator=g), torch.randn(E, 64, generator=g)
     cx, ce = torch.randn(N, 96, generator=g), torch.randn(E, 64, generator=g)
-    e = _defuse_relu_ties(ora, x, x0, e, d.edge_index, g, margin=1e-4 if n < 3000 else 3e-5, att=att)
+    e = _defuse_relu_ties(ora, x, x0, e, edge_index, g, margin=margin, att=att)
     with torch.no_grad():
-        rx, re = ora(x, d.edge_index, e, x0, att)
-        gx, ge = m(x.to(dev), d.edge_index.to(dev), e.to(dev), x0.to(dev), att.to(dev))
+        rx, re = ora(x, edge_index, e, x0, att)
+        gx, ge = m(x.to(dev), edge_index.to(dev), e.to(dev), x0.to(dev), att.to(dev))
     torch.testing.assert_close(gx.cpu(), rx, rtol=1e-4, atol=1e-4)
     torch.testing.assert_close(ge.cpu(), re, rtol=1e-4, atol=1e-4)
 
     def run(mod, dev_):
         xs = [t.clone().to(dev_).requires_grad_(True) for t in (x, x0, e, att)]
-        xn, en = mod(xs[0], d.edge_index.to(dev_), xs[2], xs[1], xs[3])
+        xn, en = mod(xs[0], edge_index.to(dev_), xs[2], xs[1], xs[3])
         ((xn * cx.to(dev_)).sum() + (en * ce.to(dev_)).sum()).backward()
         return [t.grad.cpu() for t in xs], {k_: p.grad.cpu() for k_, p in mod.named_parameters()}
 
@@ -155,7 +176,7 @@ def test_clr_layer_forward_backward_match_oracle(n, k):
         assert (got_w[k_] - ref_w[k_]).abs().max().item() <= 1e-4 * ref_w[k_].abs().max().item() + 1e-6, k_
     m.zero_grad()
     with torch.no_grad():                                         # inference forwards keep no state
-        out = m(x.to(dev), d.edge_index.to(dev), e.to(dev), x0.to(dev), att.to(dev))
+        out = m(x.to(dev), edge_index.to(dev), e.to(dev), x0.to(dev), att.to(dev))
     assert not out[0].requires_grad
 
 

@@ -219,28 +219,53 @@ def test_a_graph_struct_without_run_lists_keeps_one_row_per_edge():
 
 def test_run_tail_lists_are_exact():
     """Index work is bit-exact (north_star): `b3d_graph.past_ptr / past_rows` against a plain-Python restatement -- for a graph grouped by
-    destination the last edge of every (destination, aligned 16-edge block) run; for any other order the destination's CSR list."""
+    destination the last edge of every (destination, aligned 16-edge block) run; for any other order the destination's CSR list.  The
+    synthetic windows, then the hand-made shapes of tests/irregular_graphs.py: T1 (runs of 16 from edge 0, runs of 1 .. 64 starting
+    at many offsets inside a block), T2 (a run of 300 edges), T5 (graphs of 1 .. 129 edges) and T6 (every edge into one node)."""
+    import irregular_graphs as ig
     from batch3dmot_amd import _lib, synth
     dev = torch.device("cuda:0")
+    graphs = []
     for n, k, idx in ((37, 3, 880), (260, 7, 881), (700, 13, 882)):
-        data = synth.make_graph(n, None, k=k, graph_idx=idx)
-        ei = data.edge_index
+        graphs.append((f"synth {n}/{k}", n, synth.make_graph(n, None, k=k, graph_idx=idx).edge_index))
+    graphs += [("T1", *ig.block_runs()), ("T2", *ig.long_run()), ("T6", *ig.one_sink())]
+    graphs += [(f"T5 {n}/{e}", *ig.tiny(n, e)) for n, e in ig.TINY]
+    for name, n, ei in graphs:
         e = ei.size(1)
         g = _lib.Graph(ei.to(dev), n)
         ptr = g._view(g.c.past_ptr, n + 1).cpu().tolist()
         rows = g._view(g.c.past_rows, ptr[-1]).cpu().tolist()
-        dst = ei[1].tolist()
-        want_ptr, want_rows = [0], []
-        for node in range(n):
-            edges = [i for i in range(e) if dst[i] == node]            # contiguous: the graph is grouped by destination
-            blocks = sorted({i // 16 for i in edges})
-            want_rows += [max(i for i in edges if i // 16 == b) for b in blocks]
-            want_ptr.append(len(want_rows))
-        assert int(g._view(g.c.dst_unsorted, 1).item()) == 0 and ptr == want_ptr and rows == want_rows, (n, k)
+        want_ptr, want_rows = ig.run_tails(ei, n)
+        assert int(g._view(g.c.dst_unsorted, 1).item()) == 0 and ptr == want_ptr and rows == want_rows, name
         # the same graph with its edges reversed: not grouped by ascending destination -> the CSR lists (edge ids ascending per node)
         rev = torch.flip(ei, dims=[1]).contiguous()
         g2 = _lib.Graph(rev.to(dev), n)
+        if bool((rev[1][1:] >= rev[1][:-1]).all()):                 # (T6, E = 1: one destination -- still grouped)
+            assert int(g2._view(g2.c.dst_unsorted, 1).item()) == 0, name
+            assert g2._view(g2.c.past_ptr, n + 1).cpu().tolist() == want_ptr, name
+            continue
         a = g2.arrays()
         ptr2 = g2._view(g2.c.past_ptr, n + 1).cpu()
-        assert int(g2._view(g2.c.dst_unsorted, 1).item()) == 1
-        assert torch.equal(ptr2, a["dst_ptr"].cpu()) and torch.equal(g2._view(g2.c.past_rows, e).cpu(), a["dst_perm"].cpu())
+        assert int(g2._view(g2.c.dst_unsorted, 1).item()) == 1, name
+        assert torch.equal(ptr2, a["dst_ptr"].cpu()) and torch.equal(g2._view(g2.c.past_rows, e).cpu(), a["dst_perm"].cpu()), name
+
+
+def test_run_tail_list_flag_at_the_edges_of_grouped():
+    """`dst_unsorted` decides between the two forms: grouped by destination except for the LAST edge (one comparison across the end
+    of the list) is unsorted -- CSR lists; a single edge is grouped -- one tail."""
+    import irregular_graphs as ig
+    from batch3dmot_amd import _lib
+    dev = torch.device("cuda:0")
+    n, ei = ig.block_runs()
+    last = ei.clone()
+    last[1, -1] = 0                                                    # every other edge into nodes >= 2, in order
+    g = _lib.Graph(last.to(dev), n)
+    a = g.arrays()
+    assert int(g._view(g.c.dst_unsorted, 1).item()) == 1
+    assert torch.equal(g._view(g.c.past_ptr, n + 1).cpu(), a["dst_ptr"].cpu())
+    assert torch.equal(g._view(g.c.past_rows, last.size(1)).cpu(), a["dst_perm"].cpu())
+    one = torch.tensor([[3], [5]])
+    g1 = _lib.Graph(one.to(dev), 9)
+    assert int(g1._view(g1.c.dst_unsorted, 1).item()) == 0
+    assert g1._view(g1.c.past_ptr, 10).cpu().tolist() == [0] * 6 + [1] * 4
+    assert g1._view(g1.c.past_rows, 1).cpu().tolist() == [0]

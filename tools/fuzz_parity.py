@@ -3,7 +3,7 @@ size and degree -- edge counts that are not multiples of the 64-row tiles, a han
 against the CPU oracle, plus bitwise repeatability of the HIP side.  Prints one line per case and the worst errors; exit status 1
 on a violation.  ``run_cases`` is what tests/test_fuzz_parity_hip.py runs on a 12-case seeded subset (round 6).
 
-    python tools/fuzz_parity.py [--cases 24] [--seed 0]
+    python tools/fuzz_parity.py [--cases 24] [--seed 0] [--topology grouped|irregular]
 """
 import argparse, os, sys
 import torch
@@ -27,8 +27,41 @@ def grads(model, data, w):
     return out.detach(), xs.detach(), {n: (p.grad.detach().clone() if p.grad is not None else None) for n, p in model.named_parameters()}
 
 
-def run_cases(cases=24, seed=0, max_nodes=700, out=print):
-    """Returns (failures, worst output error, worst gradient L2 error)."""
+def make_irregular(data, case, seed):
+    """topology="irregular": the synthetic window plus a hub of in-degree 20 .. 300 and/or a source of out-degree 20 .. 300 (random
+    endpoints, duplicates allowed; new edges get seeded float64 attributes), grouped by destination again -- and in every other case
+    of each model the whole edge order shuffled (the graph build's one-row-per-edge form).  Returns a note for the case's line."""
+    g = torch.Generator().manual_seed(100003 * seed + 7919 * case + 1)
+    n, e0 = data.pose_feats.size(0), data.edge_index.size(1)
+    kind = int(torch.randint(0, 3, (1,), generator=g))                   # 0 hub, 1 high-out-degree source, 2 both
+    new, note = [], []
+    if kind in (0, 2):
+        h, deg = int(torch.randint(0, n, (1,), generator=g)), int(torch.randint(20, 301, (1,), generator=g))
+        new.append(torch.stack([torch.randint(0, n, (deg,), generator=g), torch.full((deg,), h, dtype=torch.long)]))
+        note.append(f"hub in {deg}")
+    if kind in (1, 2):
+        s_, deg = int(torch.randint(0, n, (1,), generator=g)), int(torch.randint(20, 301, (1,), generator=g))
+        new.append(torch.stack([torch.full((deg,), s_, dtype=torch.long), torch.randint(0, n, (deg,), generator=g)]))
+        note.append(f"hub out {deg}")
+    ei = torch.cat([data.edge_index] + new, 1)
+    e_new = ei.size(1) - e0
+    extra = {"edge_attr": torch.randn(e_new, 4, generator=g, dtype=torch.float64), "y": torch.zeros(e_new, dtype=data.y.dtype),
+             "edge_weights": torch.ones(e_new, dtype=data.edge_weights.dtype), "edge_classes": torch.ones(e_new, dtype=data.edge_classes.dtype)}
+    if (case // 2) % 2 == 1:
+        order = torch.randperm(ei.size(1), generator=g)
+        note.append("shuffled")
+    else:
+        order = torch.argsort(ei[1], stable=True)
+    data.edge_index = ei[:, order].contiguous()
+    for k, v in extra.items():
+        setattr(data, k, torch.cat([getattr(data, k), v], 0)[order].contiguous())
+    return "  [" + ", ".join(note) + "]"
+
+
+def run_cases(cases=24, seed=0, max_nodes=700, out=print, topology="grouped"):
+    """Returns (failures, worst output error, worst gradient L2 error).  topology: "grouped" (the synthetic windows as built: edges
+    grouped by destination, in-degree < 14) or "irregular" (make_irregular)."""
+    assert topology in ("grouped", "irregular"), topology
     from oracle import ref_encoders, ref_torch            # checker only
     from oracle.seeded import seeded_fill_
     from batch3dmot_amd import encoders, synth
@@ -43,6 +76,7 @@ def run_cases(cases=24, seed=0, max_nodes=700, out=print):
         n = int(torch.randint(12, max_nodes, (1,), generator=gen))
         k = int(torch.randint(2, 14, (1,), generator=gen))
         data = synth.make_graph(n, None, k=k, graph_idx=7000 + case, modalities=(kind == "clr"))
+        topo_note = make_irregular(data, case, seed) if topology == "irregular" else ""
         if kind == "clr" and case % 6 == 2:
             data.radar_feats.zero_()                      # camera + LiDAR only
         if kind == "clr" and case % 6 == 4:
@@ -129,7 +163,7 @@ def run_cases(cases=24, seed=0, max_nodes=700, out=print):
         bad += 0 if ok else 1
         worst_out, worst_l2 = max(worst_out, e_out, e_x), max(worst_l2, gl2)
         out(f"{kind:4s} N {n:4d} E {E:5d} (E % 64 = {E % 64:2d})  out {e_out:.1e}  x {e_x:.1e}  worst grad L2 {gl2:.1e} ({gname})  "
-              f"repeatable {same}  {'ok' if ok else 'FAIL'}{note}")
+              f"repeatable {same}  {'ok' if ok else 'FAIL'}{note}{topo_note}")
     return bad, worst_out, worst_l2
 
 
@@ -137,7 +171,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=24)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--topology", choices=("grouped", "irregular"), default="grouped")
     a = ap.parse_args()
-    bad, worst_out, worst_l2 = run_cases(a.cases, a.seed, out=lambda s_: print(s_, flush=True))
+    bad, worst_out, worst_l2 = run_cases(a.cases, a.seed, out=lambda s_: print(s_, flush=True), topology=a.topology)
     print(f"cases {a.cases}  failures {bad}  worst output error {worst_out:.2e}  worst gradient L2 error {worst_l2:.2e}")
     sys.exit(1 if bad else 0)
